@@ -1,8 +1,21 @@
 """Benchmark: plainCV training hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
                     [--workload vit_c2_f32|vit_c2|vit_c4_soap|vit_c4_shampoo|lm124m|lm420m]
-                    [--no-cpu-baseline] [--no-sub] [--no-lm] [--shard-opt]
+                    [--full [--no-cpu-baseline] [--no-roofline] [--no-sub] [--no-lm]] [--shard-opt]
+
+A plain run does only what its headline figure needs: set up, W warm-up steps, K timed steps, the
+JSON line (``value`` and ``ms_per_step`` of the selected workload; ``roofline`` and ``cpu_baseline``
+are null).  ``--full`` adds everything else described below -- the sub-lines, the live roofline
+launches, the CPU baselines and (N > 1) the all-reduce / optimizer-step timings -- each of which
+``--no-sub`` / ``--no-lm`` / ``--no-roofline`` / ``--no-cpu-baseline`` can switch off again.
+
+``--dump-outputs DIR`` writes what the timed path computed in its last timed step, as rank 0 holds
+it after the timed region: ``DIR/metrics.npy`` (the step's returned metrics), ``DIR/params.npy`` (the
+flat fp32 parameters after the step's update) and, for the ViT workloads, ``DIR/grads.npy`` (the last
+step's flat gradients), all float32.  An array over its share of 64 MB is written as a fixed, seeded
+sample of its elements.  Parameters, batches and dropout seeds are seeded, so two runs with the same
+arguments see identical inputs.
 
 ``--gpus N`` (N > 1) without a torchrun environment: the parent process spawns N ranks of this
 script (RANK/LOCAL_RANK/WORLD_SIZE/MASTER_ADDR=127.0.0.1/MASTER_PORT, one GPU each) BEFORE
@@ -17,14 +30,14 @@ computes in fp32; the reference has no dtype knob).  One "step" = one full optim
 in HBM.  With N>1 each rank runs the same per-GPU batch (weak scaling) and gradients are averaged
 over RCCL once per step.  ``value`` = images/s over all ranks.
 
-Sub-lines of the default run (``--no-sub`` skips them, ``--no-lm`` only the LM ones), each with its
+Sub-lines of the default ``--full`` run (``--no-sub`` skips them, ``--no-lm`` only the LM ones), each with its
 own roofline and (N=1) CPU baseline: ``vit_c2_bf16`` (the same workload with bf16 MFMA operands,
 configs[1]'s wording), ``vit_c4_soap`` / ``vit_c4_shampoo`` (configs[3]'s optimizers, fp32),
 ``lm124m`` (configs[2]: 124M LM, AdamW, seq 1024, micro-batch 16, accumulation 8) and ``lm420m``
 (configs[4]: tr_420M_x8gpu.yaml shape, Muon, seq 2048, micro-batch 8, accumulation 4, clip 1.0); the
 LM lines are DDP runs over the same ranks.
 
-Also reported: the roofline of the dominant kernel (the kernel family with the largest measured
+Also reported under ``--full``: the roofline of the dominant kernel (the kernel family with the largest measured
 share of the step, timed live with HIP events on its own stream; algorithmic bytes or FLOPs per
 launch) and the CPU baseline (the oracle/ restatement timed on this host's cores on a bounded sample).
 """
@@ -331,6 +344,24 @@ def optimizer_ms(tx, store, opt_state, gscale=None, iters=5):
             "shard": sh.describe() if sh is not None else None}
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write {name: device tensor} as path/<name>.npy (float32), at most
+    DUMP_BUDGET_BYTES in all.  The budget is split evenly; an array over its share is written as a
+    sample at fixed indices (sorted draws of a generator seeded by the array's length)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // len(arrays) // 4
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > share:
+            g = torch.Generator().manual_seed(t.numel())
+            idx = torch.randint(0, t.numel(), (share,), generator=g).sort().values
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.to(torch.float32).cpu().numpy())
+
+
 def vit_dtype_label(cfg, state):
     """The arithmetic the step computes in.  The fp32 runner's Muon Newton-Schulz chain runs on bf16
     MFMA operands unless the optimizer reports an fp32 chain (optim/muon.py ns_dtype)."""
@@ -385,6 +416,10 @@ def bench_vit(args):
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
     dt = float(t.item())
     loss = float(step.metrics[0].item())
+    if rank == 0 and args.dump_outputs:   # before the roofline launches below reuse the step's buffers
+        n = state.params.layout.size
+        dump_outputs(args.dump_outputs, {"metrics": step.metrics, "params": state.params.flat[:n],
+                                         "grads": state.params.grad_flat[:n]})
     runner = state.runner_for(shape)
     flops = runner.flops_per_step()
     executed = getattr(runner, "executed_flops_per_step", runner.flops_per_step)()
@@ -423,8 +458,9 @@ def bench_vit(args):
             out["cpu_baseline"] = cpu_baseline_vit(cfg, **cpu_sample(args))
         else:
             out["cpu_baseline"] = None
-    ar = allreduce_busbw(state.params.grad_flat[: state.params.layout.size]) if world > 1 else None
-    om = optimizer_ms(state.tx, state.params, state.opt_state) if world > 1 else None
+    extras = world > 1 and args.full
+    ar = allreduce_busbw(state.params.grad_flat[: state.params.layout.size]) if extras else None
+    om = optimizer_ms(state.tx, state.params, state.opt_state) if extras else None
     if out is not None and world > 1:
         out["grad_allreduce"] = ar
         out["optimizer_step_per_rank"] = om
@@ -504,9 +540,12 @@ def bench_lm(args):
     gen = torch.Generator().manual_seed(99 + rank)
     pool = torch.randint(0, cfg.vocab_size, (4, mb, cfg.seq_len + 1), generator=gen, dtype=torch.int32).to(dev)
 
+    last = None   # the last micro-step's metrics (the runner's buffer)
+
     def one_step(i):
+        nonlocal last
         for a in range(accum):
-            compute_grads(st, pool[(i * accum + a) % 4])
+            last = compute_grads(st, pool[(i * accum + a) % 4])
         apply_grads(st)
 
     for i in range(args.warmup):
@@ -527,8 +566,11 @@ def bench_lm(args):
     dt = float(t.item())
     tokens = world * mb * accum * cfg.seq_len * args.steps
     fpt = model.flops_per_token(cfg.seq_len)
-    ar = allreduce_busbw(st.params.grad_flat[: st.params.layout.size], iters=3) if world > 1 else None
-    om = optimizer_ms(st.tx, st.params, st.opt_state) if world > 1 else None
+    if rank == 0 and args.dump_outputs and last is not None:
+        dump_outputs(args.dump_outputs, {"metrics": last, "params": st.params.flat[: st.params.layout.size]})
+    extras = world > 1 and args.full
+    ar = allreduce_busbw(st.params.grad_flat[: st.params.layout.size], iters=3) if extras else None
+    om = optimizer_ms(st.tx, st.params, st.opt_state) if extras else None
     if rank != 0:
         return None
     return {"metric": METRIC, "value": round(tokens / dt, 1), "unit": "tokens/s", "n_gpus": world,
@@ -678,13 +720,18 @@ SUB_LINES = [("vit_c2_bf16", "vit_c2"), ("vit_c4_soap", "vit_c4_soap"), ("vit_c4
              ("lm124m", "lm124m"), ("lm420m", "lm420m")]
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="vit_c2_f32",
                     choices=["vit_c2_f32", "vit_c2", "vit_c4_soap", "vit_c4_shampoo", "lm124m", "lm420m", "dp_stub"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: sub-lines, live rooflines, CPU "
+                         "baselines, all-reduce / optimizer-step timings (the --no-* options narrow it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (metrics, params, grads) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true",
                     help="skip the live roofline launches (profiling runs: keeps timing launches out of the trace)")
@@ -697,7 +744,14 @@ def main():
     ap.add_argument("--lm-warmup", type=int, default=2)
     ap.add_argument("--shard-opt", action="store_true",
                     help="split muon/soap/shampoo per-matrix work across the DP ranks (optim/sharding.py)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if not args.full:   # a plain run: the headline figure only
+        args.no_sub = args.no_roofline = args.no_cpu_baseline = True
+    return args
+
+
+def main():
+    args = parse_args()
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -715,7 +769,7 @@ def main():
                 if args.no_lm and wl.startswith("lm"):
                     continue
                 a2 = argparse.Namespace(**vars(args))
-                a2.workload = wl
+                a2.workload, a2.dump_outputs = wl, None
                 if wl.startswith("lm"):
                     a2.steps, a2.warmup, a2.lm_micro_batch, a2.lm_accum = args.lm_steps, args.lm_warmup, None, None
                     sub = bench_lm(a2)

@@ -3,7 +3,8 @@
 #   tools/gpu_pass.sh TAG "PYTEST_ARGS" "BENCH_ARGS"
 # PYTEST_ARGS: test selection (e.g. "tests -m gpu", "tests/test_x.py -k y"), "" skips the tests;
 # "smoke" as the 4th argument also runs __graft_entry__.smoke(); BENCH_ARGS: bench.py arguments,
-# "-" skips the bench.  Every GPU step has its own time limit and a failure ends the pass.
+# "-" skips the bench ("--full" among them adds the sub-lines, rooflines and CPU baselines to the
+# summary).  Every GPU step has its own time limit and a failure ends the pass.
 set -o pipefail
 TAG=${1:?tag}
 TESTS=${2:-}
