@@ -627,6 +627,27 @@ int pcv_muon_step_fused(const void* mats, int nmats, const void* chunks, int nch
                         int* ticket, void* stream);
 int pcv_muon_ns_fused(const void* mats, int nmats, float eps, float ns_a, float ns_b, float ns_c, int ns_steps,
                       void* stream);
+/* Muon's Newton-Schulz chain in exact fp32 (csrc/muon_ns_f32.hip; Muon(ns_dtype="float32")), three
+ * launches per iteration over 32 x 32 tiles of every routed matrix.  recs: nmats records of
+ * pcv_muon_ns_f32_rec_size() bytes {float *x0, *x1, *A, *B, *out; const double* norm2; int32 r, c, ldx,
+ * lda}: r <= c the NS operand's shape, x0 (un-normalised, from pcv_muon_prep with nnorm = 0, or from
+ * pcv_muon_grad_phase) / x1 / out [r][ldx], A / B [r][lda], ldx and lda multiples of 4 floats, all
+ * 16-byte aligned, norm2 the record's MUON_NSLOT norm slots.  tiles: {int32 mat, tm, tn, 0} records with
+ * T = pcv_muon_ns_f32_tile(): first the nsym tiles tm <= tn < ceil(r / T) of every matrix, then the
+ * nupd tiles tm < ceil(r / T), tn < ceil(c / T).  Writes out = NS_{ns_steps}(x0 / (||x0||_F + eps));
+ * ns_steps = 0 only normalises.  No atomics, no host reads, no allocation: capturable. */
+int pcv_muon_ns_f32_rec_size(void);
+int pcv_muon_ns_f32_tile(void);
+int pcv_muon_ns_f32(const void* recs, int nmats, const void* tiles, int nsym, int nupd, float eps, float ns_a,
+                    float ns_b, float ns_c, int ns_steps, void* stream);
+/* pcv_muon_apply / pcv_muon_apply_dual / pcv_muon_dual_dot over records whose xo points to fp32 X_ns
+ * (the out of the fp32 chain above, row stride ldx) instead of bf16. */
+int pcv_muon_apply_f32(const void* mats, int nmats, int64_t max_elems, float lr, float wd, int shape_scale,
+                       int apply, void* stream);
+int pcv_muon_apply_dual_f32(const void* mats, int nmats, int64_t max_elems, float lr, float wd, int shape_scale,
+                            int apply, const double* dual, void* stream);
+int pcv_muon_dual_dot_f32(const void* mats, int nmats, int64_t max_elems, float beta, int nesterov,
+                          const int* step, const float* gscale, double* dual, void* stream);
 int pcv_chunk_size(void);
 
 /* ------------------------------------------------- matrix preconditioners ----

@@ -241,10 +241,13 @@ __global__ __launch_bounds__(256) void muon_norm_kernel(const MuonMat* mats, flo
 // muon_adaptive (optax.contrib.muon adaptive=True): dual[m] += <mu_hat, O>_F, the dual norm that
 // scales the orthogonalised update (arXiv 2409.20325).  mu_hat is re-formed from the updated mu and
 // g exactly as muon_prep formed it (the step counter is bumped only after the apply launch).
+// XT: element type of X_ns behind M.xo -- bf16 (the bf16 NS paths) or float (csrc/muon_ns_f32.hip)
+template <typename XT>
 __global__ __launch_bounds__(256) void muon_dual_dot_kernel(const MuonMat* mats, MuonHyper h, const int* step,
                                                             const float* gscale, double* dual) {
   __shared__ float red[4];
   const MuonMat M = mats[blockIdx.y];
+  const XT* xo = reinterpret_cast<const XT*>(M.xo);
   const int64_t n = M.rows * M.cols;
   const float t = (float)(*step + 1);
   const float bc = 1.f - powf(h.beta, t), bcn = 1.f - powf(h.beta, t + 1.f);
@@ -258,17 +261,21 @@ __global__ __launch_bounds__(256) void muon_dual_dot_kernel(const MuonMat* mats,
     const float gi = M.g[off] * gs;
     const float mi = M.mu[off];
     const float xh = h.nesterov ? h.beta * mi / bcn + (1.f - h.beta) * gi / bc : mi / bc;
-    s += xh * bf2f(M.xo[tr ? (int64_t)c * M.ldx + r : (int64_t)r * M.ldx + c]);
+    s += xh * (float)xo[tr ? (int64_t)c * M.ldx + r : (int64_t)r * M.ldx + c];
   }
   s = block_sum(s, red);
   if (threadIdx.x == 0) atomicAdd(dual + blockIdx.y, (double)s);
 }
 
 // u = -lr*(O*[dual]*shape_scale + wd*p); p += u   (4 elements per thread, loads first, as muon_prep)
+template <typename XT>
 __global__ __launch_bounds__(256) void muon_apply_kernel(const MuonMat* mats, MuonHyper h) {
   const MuonMat M = mats[blockIdx.y];
   const int n = (int)(M.rows * M.cols);
-  const bool tr = M.rows > M.cols, v4 = muon_v4(M);
+  const XT* xo = reinterpret_cast<const XT*>(M.xo);
+  // fp32 X_ns rows are read as float4
+  const bool tr = M.rows > M.cols,
+             v4 = muon_v4(M) && (sizeof(XT) == 2 || (reinterpret_cast<uintptr_t>(M.xo) & 15) == 0);
   const float ss = (h.shape_scale > 0.f ? sqrtf(fmaxf(1.f, (float)M.cols / (float)M.rows)) : 1.f) *
                    (h.dual ? (float)h.dual[blockIdx.y] : 1.f);
   const int cols = (int)M.cols;
@@ -292,13 +299,18 @@ __global__ __launch_bounds__(256) void muon_apply_kernel(const MuonMat* mats, Mu
       }
     }
     if (v4 && !tr) {
-      const bf16x4 x4 = *reinterpret_cast<const bf16x4*>(M.xo + (int64_t)rr[0] * M.ldx + cc[0]);
+      if constexpr (sizeof(XT) == 2) {
+        const bf16x4 x4 = *reinterpret_cast<const bf16x4*>(xo + (int64_t)rr[0] * M.ldx + cc[0]);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = bf2f(x4[e]);
+        for (int e = 0; e < 4; ++e) o[e] = bf2f(x4[e]);
+      } else {
+        const float4 x4 = *reinterpret_cast<const float4*>(xo + (int64_t)rr[0] * M.ldx + cc[0]);
+        o[0] = x4.x; o[1] = x4.y; o[2] = x4.z; o[3] = x4.w;
+      }
     } else {
 #pragma unroll
       for (int e = 0; e < 4; ++e)
-        o[e] = bf2f(M.xo[tr ? (int64_t)cc[e] * M.ldx + rr[e] : (int64_t)rr[e] * M.ldx + cc[e]]);
+        o[e] = (float)xo[tr ? (int64_t)cc[e] * M.ldx + rr[e] : (int64_t)rr[e] * M.ldx + cc[e]];
     }
     float u[4], pn[4];
 #pragma unroll
@@ -414,15 +426,28 @@ extern "C" int pcv_muon_grad_phase(const void* mats, int nmats, int64_t max_elem
   return pcv_launch_status();
 }
 
-extern "C" int pcv_muon_dual_dot(const void* mats, int nmats, int64_t max_elems, float beta, int nesterov,
-                                 const int* step, const float* gscale, double* dual, void* stream) {
-  if (nmats <= 0 || max_elems >= (1ll << 31) || !step || !dual) return PCV_EINVAL;
+template <typename XT>
+static int muon_dual_dot_launch(const void* mats, int nmats, int64_t max_elems, float beta, int nesterov,
+                                const int* step, const float* gscale, double* dual, void* stream) {
   MuonHyper h{beta, 0.f, 0.f, 0.f, 0.f, nesterov, 0, nullptr};
   int gx = (int)((max_elems + 256 * 8 - 1) / (256 * 8));
   gx = gx < 1 ? 1 : (gx > 256 ? 256 : gx);
-  hipLaunchKernelGGL(muon_dual_dot_kernel, dim3(gx, nmats), dim3(256), 0, (hipStream_t)stream, (const MuonMat*)mats,
-                     h, step, gscale, dual);
+  hipLaunchKernelGGL(muon_dual_dot_kernel<XT>, dim3(gx, nmats), dim3(256), 0, (hipStream_t)stream,
+                     (const MuonMat*)mats, h, step, gscale, dual);
   return pcv_launch_status();
+}
+
+extern "C" int pcv_muon_dual_dot(const void* mats, int nmats, int64_t max_elems, float beta, int nesterov,
+                                 const int* step, const float* gscale, double* dual, void* stream) {
+  if (nmats <= 0 || max_elems >= (1ll << 31) || !step || !dual) return PCV_EINVAL;
+  return muon_dual_dot_launch<bf16>(mats, nmats, max_elems, beta, nesterov, step, gscale, dual, stream);
+}
+
+// the *_f32 forms: each record's xo points to fp32 X_ns (pcv_muon_ns_f32's out), same row stride ldx
+extern "C" int pcv_muon_dual_dot_f32(const void* mats, int nmats, int64_t max_elems, float beta, int nesterov,
+                                     const int* step, const float* gscale, double* dual, void* stream) {
+  if (!mats || nmats <= 0 || max_elems >= (1ll << 31) || !step || !dual) return PCV_EINVAL;
+  return muon_dual_dot_launch<float>(mats, nmats, max_elems, beta, nesterov, step, gscale, dual, stream);
 }
 
 extern "C" int pcv_muon_apply_dual(const void* mats, int nmats, int64_t max_elems, float lr, float wd,
@@ -438,8 +463,25 @@ extern "C" int pcv_muon_apply_dual(const void* mats, int nmats, int64_t max_elem
   MuonHyper h{0.f, lr, wd, 0.f, shape_scale ? 1.f : 0.f, 0, apply, dual};
   int gx = (int)((max_elems + 256 * 4 - 1) / (256 * 4));   // one 4-element group per thread
   gx = gx < 1 ? 1 : (gx > 1024 ? 1024 : gx);
-  hipLaunchKernelGGL(muon_apply_kernel, dim3(gx, nmats), dim3(256), 0, (hipStream_t)stream, (const MuonMat*)mats, h);
+  hipLaunchKernelGGL(muon_apply_kernel<bf16>, dim3(gx, nmats), dim3(256), 0, (hipStream_t)stream,
+                     (const MuonMat*)mats, h);
   return pcv_launch_status();
+}
+
+extern "C" int pcv_muon_apply_dual_f32(const void* mats, int nmats, int64_t max_elems, float lr, float wd,
+                                       int shape_scale, int apply, const double* dual, void* stream) {
+  if (!mats || nmats <= 0 || max_elems >= (1ll << 31)) return PCV_EINVAL;
+  MuonHyper h{0.f, lr, wd, 0.f, shape_scale ? 1.f : 0.f, 0, apply, dual};
+  int gx = (int)((max_elems + 256 * 4 - 1) / (256 * 4));   // as pcv_muon_apply_dual
+  gx = gx < 1 ? 1 : (gx > 1024 ? 1024 : gx);
+  hipLaunchKernelGGL(muon_apply_kernel<float>, dim3(gx, nmats), dim3(256), 0, (hipStream_t)stream,
+                     (const MuonMat*)mats, h);
+  return pcv_launch_status();
+}
+
+extern "C" int pcv_muon_apply_f32(const void* mats, int nmats, int64_t max_elems, float lr, float wd, int shape_scale,
+                                  int apply, void* stream) {
+  return pcv_muon_apply_dual_f32(mats, nmats, max_elems, lr, wd, shape_scale, apply, nullptr, stream);
 }
 
 extern "C" int pcv_muon_mat_size(void) { return (int)sizeof(MuonMat); }

@@ -147,6 +147,12 @@ SIGNATURES = {
     "pcv_muon_step_fused": [P, I32, P, I32, P, P, P, P, P, P, F32, F32, F32, I32, F32, I32, F32, F32, F32, I32, F32,
                             F32, F32, F32, I32, P, P, P, P],
     "pcv_muon_ns_fused": [P, I32, F32, F32, F32, F32, I32, P],
+    "pcv_muon_ns_f32": [P, I32, P, I32, I32, F32, F32, F32, F32, I32, P],
+    "pcv_muon_ns_f32_rec_size": [],
+    "pcv_muon_ns_f32_tile": [],
+    "pcv_muon_apply_f32": [P, I32, I64, F32, F32, I32, I32, P],
+    "pcv_muon_apply_dual_f32": [P, I32, I64, F32, F32, I32, I32, P, P],
+    "pcv_muon_dual_dot_f32": [P, I32, I64, F32, I32, P, P, P, P],
     "pcv_muon_norm_slots": [],
     "pcv_muon_fused_ok": [I64, I64],
     "pcv_transpose_bf16_batch": [P, I32, I64, P],

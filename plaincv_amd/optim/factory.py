@@ -18,6 +18,10 @@ Build-only key ``shard_optimizer`` (default False: every replica runs every matr
 reference): True splits muon / soap / shampoo's per-matrix work across the data-parallel ranks
 (optim/sharding.py; SURVEY §8e second stage); same updates, bit-identical replicas.
 
+Build-only key ``muon_ns_dtype`` (default "bfloat16": Newton-Schulz on bf16 MFMA operands, X carried
+in fp32): "float32" runs muon's Newton-Schulz chain in exact fp32, the reference's arithmetic
+(csrc/muon_ns_f32.hip; slower and more workspace); anything else raises ``ValueError``.
+
 Any other name raises ``ValueError(f"Unknown optimizer name: {cfg.optim}")``
 (factory.py:797-798); the research optimizers of the reference (PN-S, Sophia,
 HF) are out of scope.
@@ -61,7 +65,8 @@ def _base_optimizer(cfg):
                     eps=_g(cfg, "eps", 1e-8), weight_decay=wd, nesterov=bool(_g(cfg, "muon_nesterov", True)),
                     adaptive=bool(_g(cfg, "muon_adaptive", False)),
                     adam_b1=_g(cfg, "beta1", 0.9), adam_b2=_g(cfg, "beta2", 0.999),
-                    adam_eps_root=_g(cfg, "adam_eps_root", 0.0), adam_weight_decay=wd, shard=_shard(cfg))
+                    adam_eps_root=_g(cfg, "adam_eps_root", 0.0), adam_weight_decay=wd, shard=_shard(cfg),
+                    ns_dtype=str(_g(cfg, "muon_ns_dtype", "bfloat16")))
     if name == "soap":
         return Soap(lr, b1=_g(cfg, "beta1", 0.95), b2=_g(cfg, "beta2", 0.95), eps=_g(cfg, "eps", 1e-8),
                     weight_decay=_g(cfg, "weight_decay", 0.01),

@@ -21,6 +21,11 @@ are one launch each over all routed matrices.  Matrices whose NS operand fits
 one workgroup's LDS (min <= 128, max <= 256: every ViT-small kernel) skip
 the GEMM chain: pcv_muon_ns_fused runs all iterations for each of them in one
 workgroup with X, A, B resident in LDS -- one launch for all such matrices.
+
+``ns_dtype="float32"`` (opt-in; factory key ``muon_ns_dtype``) runs the chain in the reference's own
+arithmetic instead: exact fp32 MFMA, three launches per iteration (A = X X^T; B = b A + c A A;
+X' = a X + B X) over 32 x 32 tiles of ALL routed matrices at once (csrc/muon_ns_f32.hip), no groups,
+fp32 X_ns read by the fp32 forms of the apply / dual-dot launches.  Cost and accuracy: DESIGN.md §5.3.
 """
 from collections import OrderedDict
 
@@ -59,7 +64,12 @@ class _Group:
 class Muon(GradientTransformation):
     def __init__(self, learning_rate, ns_coeffs=(3.4445, -4.7750, 2.0315), ns_steps=5, beta=0.95, eps=1e-8,
                  weight_decay=0.0, nesterov=True, adaptive=False, adam_b1=0.9, adam_b2=0.999, adam_eps_root=0.0,
-                 adam_weight_decay=0.0, shape_scale=True, fused=True, shard=None):
+                 adam_weight_decay=0.0, shape_scale=True, fused=True, shard=None, ns_dtype="bfloat16"):
+        # "float32": the Newton-Schulz chain in the reference's own arithmetic (exact fp32 MFMA,
+        # csrc/muon_ns_f32.hip) instead of bf16 MFMA operands; opt-in, DESIGN.md §5.3
+        if ns_dtype not in ("bfloat16", "float32"):
+            raise ValueError(f"Unknown muon ns_dtype: {ns_dtype!r} (expected 'bfloat16' or 'float32')")
+        self.ns_dtype = ns_dtype
         # muon_adaptive (factory.py:457,475): O <- <mu_hat, O>_F O before the shape scale, one
         # pcv_muon_dual_dot launch between NS and the apply launch (the one-launch step is skipped)
         self.adaptive = bool(adaptive)
@@ -96,7 +106,11 @@ class Muon(GradientTransformation):
         for k in routed:
             r, c = store.params[k].shape
             groups.setdefault((min(r, c), max(r, c)), []).append(k)
-        gl = [_Group(r, c, names, dev) for (r, c), names in groups.items()]
+        f32 = self.ns_dtype == "float32"
+        # the fp32 chain has no groups: one tile table over all routed matrices (_init_f32)
+        gl = [] if f32 else [_Group(r, c, names, dev) for (r, c), names in groups.items()]
+        # the split step's size limit (min <= 128, max <= 256) holds for both NS dtypes
+        st.split_shapes = self.fused and all(bool(lib.pcv_muon_fused_ok(r, c)) for r, c in groups)
         for g in gl:
             g.fused = self.fused and bool(lib.pcv_muon_fused_ok(g.r, g.c))
         st.groups = [g for g in gl if not g.fused] + [g for g in gl if g.fused]
@@ -116,6 +130,10 @@ class Muon(GradientTransformation):
         assert size == 13 * 8, size
         recs_apply, recs_upd = [], []
         idx = 0
+        tab = lambda recs: torch.tensor(np.array(recs, dtype=np.uint64).view(np.int64), device=dev)  # noqa: E731
+        if f32:
+            self._init_f32(store, st, lib, tab)
+            return st
         for g in st.groups:
             for j, k in enumerate(g.names):
                 leaf = store.leaf(k)
@@ -129,10 +147,51 @@ class Muon(GradientTransformation):
                 recs_apply.append(base + [0] + tail)
                 recs_upd.append(base + [st.upd.data_ptr() + off * 4] + tail)
                 idx += 1
-        tab = lambda recs: torch.tensor(np.array(recs, dtype=np.uint64).view(np.int64), device=dev)  # noqa: E731
         st.mats_apply = tab(recs_apply) if routed else None
         st.mats_upd = tab(recs_upd) if routed else None
         return st
+
+    def _init_f32(self, store, st, lib, tab):
+        """ns_dtype="float32": per routed matrix fp32 X ping-pong, A, B and the fixed X_ns output, all
+        carved from one zeroed workspace (allocated here, never again); one NS record and the tiles
+        of both tilings per matrix (csrc/muon_ns_f32.hip).  The MuonMat records (prep, apply, dual
+        dot) point x32 at the ping-pong's first half and xo at the fp32 output."""
+        routed, mu = st.routed, st.tensors["mu"]
+        assert lib.pcv_muon_ns_f32_rec_size() == 64
+        T = int(lib.pcv_muon_ns_f32_tile())
+        shapes, off = [], 0
+        for k in routed:
+            rows, cols = store.leaf(k).shape
+            r, c = min(rows, cols), max(rows, cols)
+            ldx, lda = (c + 7) // 8 * 8, (r + 7) // 8 * 8
+            offs = []
+            for n in (r * ldx, r * ldx, r * lda, r * lda, r * ldx):     # x0, x1, A, B, out
+                offs.append(off)
+                off += (n + 63) // 64 * 64                              # 256-byte aligned
+            shapes.append((r, c, ldx, lda, offs))
+        st.ns_ws = torch.zeros(max(1, off), dtype=torch.float32, device=store.device)
+        base_ws = st.ns_ws.data_ptr()
+        recs_apply, recs_upd, recs_ns, sym, upd = [], [], [], [], []
+        for idx, (k, (r, c, ldx, lda, offs)) in enumerate(zip(routed, shapes)):
+            leaf = store.leaf(k)
+            rows, cols = leaf.shape
+            off = leaf.offset
+            x0, x1, A, B, out = (base_ws + 4 * o for o in offs)
+            norm2 = st.norm2.data_ptr() + idx * st.nslot * 8
+            base = [store.flat.data_ptr() + off * 4, store.grad_flat.data_ptr() + off * 4,
+                    mu.data_ptr() + off * 4, store.shadow.data_ptr() + off * 2]
+            tail = [rows, cols, leaf.strides[0], ldx, x0, 0, out, norm2]
+            recs_apply.append(base + [0] + tail)
+            recs_upd.append(base + [st.upd.data_ptr() + off * 4] + tail)
+            recs_ns.append([x0, x1, A, B, out, norm2, r | (c << 32), ldx | (lda << 32)])
+            tr, tc = (r + T - 1) // T, (c + T - 1) // T
+            sym += [(idx, i, j, 0) for i in range(tr) for j in range(i, tr)]
+            upd += [(idx, i, j, 0) for i in range(tr) for j in range(tc)]
+        st.mats_apply = tab(recs_apply) if routed else None
+        st.mats_upd = tab(recs_upd) if routed else None
+        st.ns_recs = tab(recs_ns) if routed else None
+        st.ns_nsym, st.ns_nupd = len(sym), len(upd)
+        st.ns_tiles = torch.tensor(np.array(sym + upd, dtype=np.int32).reshape(-1, 4), device=store.device)
 
     # ------------------------------------------------------------------
     def _newton_schulz(self, st):
@@ -151,7 +210,34 @@ class Muon(GradientTransformation):
             hip.call("pcv_muon_ns_fused", ptr(fused_recs), st.n_fused, self.eps, a, b, c, self.ns_steps,
                      stream_ptr())
 
+    def _ns_f32(self, st):
+        """3 x ns_steps phase launches over the tile table (ns_steps = 0: one scale-only launch); reads
+        the un-normalised X and its norm slots, leaves fp32 X_ns in the records' output buffers."""
+        hip.call("pcv_muon_ns_f32", ptr(st.ns_recs), len(st.routed), ptr(st.ns_tiles), st.ns_nsym, st.ns_nupd,
+                 self.eps, self.a, self.b, self.c, self.ns_steps, stream_ptr())
+
+    def _run_f32(self, store, st, gscale, apply):
+        # prep -> NS phases -> [dual dot] -> apply -> Adam branch -> step bump: a fixed launch sequence
+        if st.routed:
+            n = len(st.routed)
+            hip.call("pcv_muon_prep", ptr(st.mats_apply), n, 0, st.max_elems, self.beta, int(self.nesterov),
+                     self.eps, ptr(st.count), ptr(gscale), stream_ptr())
+            self._ns_f32(st)
+            if self.adaptive:
+                st.dual.zero_()
+                hip.call("pcv_muon_dual_dot_f32", ptr(st.mats_apply), n, st.max_elems, self.beta,
+                         int(self.nesterov), ptr(st.count), ptr(gscale), ptr(st.dual), stream_ptr())
+            hip.call("pcv_muon_apply_dual_f32", ptr(st.mats_apply if apply else st.mats_upd), n, st.max_elems,
+                     self.lr, self.wd, int(self.shape_scale), int(apply), ptr(st.dual) if self.adaptive else None,
+                     stream_ptr())
+        st.branch.run(store, st.tensors["mu"], st.tensors["nu"], st.count, self.lr, gscale=gscale,
+                      upd=None if apply else st.upd, apply=apply)
+        K.step_bump(st.count)
+        sharding.finish(st.shard, store, st, apply)
+
     def _run(self, store, st, gscale, apply):
+        if self.ns_dtype == "float32":
+            return self._run_f32(store, st, gscale, apply)
         if st.routed and st.n_general == 0 and st.vec4 and not self.adaptive:
             # every routed matrix fits the one-workgroup NS: the NS workgroups, the Adam branch and the
             # step bump share one launch (csrc/muon_fused.hip muon_step_kernel), between the wide prep
@@ -195,6 +281,8 @@ class Muon(GradientTransformation):
     # apply kernels, order-free norm slots (tests/test_vit_parity_gpu.py asserts torch.equal).
     def split_capable(self, st):
         # every routed matrix on the one-workgroup NS kernel (its NS-only blocks need no 16-B row accesses)
+        if self.ns_dtype == "float32":   # same conditions, the size limit included (st.split_shapes)
+            return bool(st.routed) and st.split_shapes and not self.adaptive and st.shard is None
         return bool(st.routed) and st.n_general == 0 and not self.adaptive and st.shard is None
 
     def step_grad_phase_(self, store, st, gscale=None):
@@ -209,6 +297,14 @@ class Muon(GradientTransformation):
         """NS + update of every routed matrix (and the step-counter bump)."""
         b1, b2, eps_root, awd = self.adam
         n = len(st.routed)
+        if self.ns_dtype == "float32":
+            # the gradient phase left X un-normalised, as the in-step prep does: the same chain, apply
+            # and bump launches as _run_f32, hence its bits
+            self._ns_f32(st)
+            hip.call("pcv_muon_apply_f32", ptr(st.mats_apply), n, st.max_elems, self.lr, self.wd,
+                     int(self.shape_scale), 1, stream_ptr())
+            K.step_bump(st.count)
+            return
         hip.call("pcv_muon_step_fused", ptr(st.mats_apply), n, None, 0, ptr(store.flat),
                  ptr(store.grad_flat), ptr(st.tensors["mu"]), ptr(st.tensors["nu"]), ptr(store.shadow), None,
                  self.lr, self.wd, self.beta, int(self.nesterov), self.eps, int(self.shape_scale), self.a, self.b,
